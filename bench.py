@@ -8,7 +8,13 @@ fused decode/env steps, instances already resident in HBM.  Weak scaling: rank r
 rows [512 r, 512 (r+1)) of ONE seed-ordered instance stream of 512 x N graphs
 (`Env(shard=(rank, world))`); the value is the whole-job aggregate.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+                    [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps in one block (`ms_per_step` =
+that block's time / K), writes its outputs if asked and prints the line.  `--dump-outputs DIR`
+writes what the last timed step returned to its caller as DIR/<name>.npy (float32; arrays above a
+fixed size as a fixed, seeded sample of their elements); the inputs are the same from run to run.
 
 `--gpus N` with N > 1 launches the N ranks itself (child processes with torchrun's environment
 variables, started before this process touches the GPU; they die with the launcher) unless it
@@ -23,7 +29,9 @@ already runs under torchrun (RANK/WORLD_SIZE set).  Workloads:
     irp40_b1024_train  configs[3] per-GPU shard: the same with the RCCL all-reduce of the
                        flat gradient; its time is reported separately
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  With `--full` (five timed blocks of K steps, the median block
+reported, unless --blocks says otherwise; --no-cpu-baseline / --no-north-star / --no-extras trim
+it) it also carries
   roofline            the decode_step kernel of the benched workload vs the HBM peak, plus
                       the loop-level (prologue + table builds + steps) and whole-rollout
                       fractions on the same algorithmic bytes
@@ -33,6 +41,9 @@ Prints ONE JSON line (rank 0).  Besides the contract keys it carries
                       ones carry roofline_train: algorithmic flops per epoch vs the ceiling of the
                       bf16-plane arithmetic, the fp32-MFMA yardstick kept as vs_fp32_mfma_peak)
   cpu_baseline        the CPU oracle (oracle/, a port of the reference) on this host
+  incl_env_reset[_device_generator]  the same rollouts with new instances drawn every step
+The training workloads carry `training` and `roofline` (from the timed epochs) either way; the
+training roofline's `dominant_kernel` (a GEMM timed on its own) needs --full.
 """
 import argparse
 import json
@@ -315,12 +326,13 @@ def sync_barrier(dist):
     torch.cuda.synchronize()
 
 
-def timed_rollouts(env, agent, greedy, steps, warmup, dist, reset=None, blocks=1):
+def timed_rollouts(env, agent, greedy, steps, warmup, dist, reset=None, blocks=1, outputs=None):
     """`blocks` blocks of EXACTLY K rollouts, each between barrier + synchronize brackets (a
-    block of 20 TSP-20 rollouts is 6 ms: one clock ramp moves it by 8 %, so the headline is the
-    median block and the spread is reported).  reset=None: instances stay resident (the
-    headline); "env": env.reset() (new instances) before every rollout.
-    Returns (list of block seconds, T, mean tour cost)."""
+    block of 20 TSP-20 rollouts is 6 ms: one clock ramp moves it by 8 %, so under --full the
+    headline is the median block and the spread is reported).  reset=None: instances stay
+    resident (the headline); "env": env.reset() (new instances) before every rollout.
+    Returns (list of block seconds, T, mean tour cost); `outputs` (a dict) receives the last
+    rollout's result tensors."""
     from agents import runtime
 
     def one():
@@ -342,16 +354,21 @@ def timed_rollouts(env, agent, greedy, steps, warmup, dist, reset=None, blocks=1
                 res = one()
             sync_barrier(dist)
             dts.append(time.perf_counter() - t0)
+    if outputs is not None:
+        outputs.update(acc_loss=res.acc_loss, acc_logp=res.acc_logp, notdone=res.notdone,
+                       emb=res.emb)
     return dts, res.T, float(-res.acc_loss.mean().item())
 
 
-def timed_training(env, agent, steps, warmup, dist, blocks=1):
+def timed_training(env, agent, steps, warmup, dist, blocks=1, outputs=None):
     """`blocks` blocks of EXACTLY K training epochs (TSPAgent.train_epoch: graph_tsp_agent.py:174-189
     of the reference), each between the same brackets.  (One block of six epochs read 56.9 ms per
     epoch instead of 17.3 on a freshly started box once: a first-touch page-in inside the timed
     region; the median block is reported and the spread kept.)  Returns (list of block seconds,
     env steps taken by all rollouts of the LAST block's epochs on this rank, rollouts per epoch,
-    mean sampled cost of the last epoch, all-reduce ms/epoch, mean steps per rollout)."""
+    mean sampled cost of the last epoch, all-reduce ms/epoch, mean steps per rollout).
+    `outputs` (a dict) receives the last epoch's loss / cost / advantage and the model's
+    parameters after it, flattened."""
     from agents import distributed, runtime
     from scipy import stats  # noqa: F401  (first import outside the timed region)
     import contextlib
@@ -365,10 +382,14 @@ def timed_training(env, agent, steps, warmup, dist, blocks=1):
             distributed.ALLREDUCE_EVENTS = evs = []
             t0 = time.perf_counter()
             for _ in range(steps):
-                _, cost, _ = agent.train_epoch(env, 1)
+                loss, cost, adv = agent.train_epoch(env, 1)
             sync_barrier(dist)
             dts.append(time.perf_counter() - t0)
     runtime.ROLLOUT_LOG = distributed.ALLREDUCE_EVENTS = None
+    if outputs is not None:
+        with torch.no_grad():
+            params = torch.cat([p.detach().reshape(-1) for p in agent.model.parameters()])
+        outputs.update(loss=loss, cost=cost, advantage=adv, params=params)
     sum_T = sum(r.T for r in log)  # env steps per graph over every rollout of the timed epochs
     ar_ms = sum(a.elapsed_time(b) for a, b in evs) / max(steps, 1)
     # an epoch's rollouts in order: sampled model, sampled baseline, greedy model, greedy baseline
@@ -719,9 +740,10 @@ def cpu_baseline(kind, N, B, greedy, budget_s=15.0):
                       f"BASELINE.md section 3)"}
 
 
-def run_workload(name, steps, warmup, device, dist, rank, world, blocks=1):
+def run_workload(name, steps, warmup, device, dist, rank, world, blocks=1, outputs=None):
     """One workload on this rank -> dict of whole-job figures (rank-reduced).  Per block the
-    time is the MAX over ranks; `seconds` is the median block."""
+    time is the MAX over ranks; `seconds` is the median block.  `outputs`: see timed_rollouts /
+    timed_training."""
     kind, N, B, mode = WORKLOADS[name]
     shard = (rank, world) if world > 1 else None
     train = mode == "train"
@@ -733,7 +755,8 @@ def run_workload(name, steps, warmup, device, dist, rank, world, blocks=1):
         distributed.broadcast_model(agent.model)
         distributed.broadcast_model(agent.target_model)
         dts, sum_T, rollouts, cost, ar_ms, (t_s, t_g) = timed_training(env, agent, steps, warmup,
-                                                                        dist, blocks=blocks)
+                                                                        dist, blocks=blocks,
+                                                                        outputs=outputs)
         dt = sorted(dts)[len(dts) // 2]   # (this rank's median block: the flop rate below)
         graph_steps = sum_T * B
         node_steps = graph_steps * N
@@ -765,7 +788,7 @@ def run_workload(name, steps, warmup, device, dist, rank, world, blocks=1):
                     "bench.training_flops_per_epoch"}
     else:
         dts, T, cost = timed_rollouts(env, agent, mode == "greedy", steps, warmup, dist,
-                                      blocks=blocks)
+                                      blocks=blocks, outputs=outputs)
         graph_steps = steps * B * T
         node_steps = graph_steps * N
     red = torch.tensor([cost, float(node_steps), float(graph_steps)], device=device,
@@ -799,6 +822,35 @@ def run_workload(name, steps, warmup, device, dist, rank, world, blocks=1):
     return out, env, agent
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs writes at most this much (the files' headers aside)
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every tensor of `outputs` as out_dir/<name>.npy, float32 (float64 stays
+    float64).  An array larger than its share of DUMP_BYTES is written as a fixed sample of its
+    flattened elements: indices drawn once from a seeded generator (seed 0), sorted, the same in
+    every run of the same workload.  Returns {name: {"shape", "sampled"}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(outputs), 1)
+    written = {}
+    for name, t in sorted(outputs.items()):
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        flat = t.reshape(-1)
+        cap = share // flat.element_size()
+        sampled = flat.numel() > cap
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = {"shape": list(t.shape), "sampled": int(cap) if sampled else None}
+    return written
+
+
 def bind_device(local):
     """This rank's GPU, in the order the library depends on: make it torch's (and HIP's) current
     device, check that it is, and only then let the library look at it -- its residency census and
@@ -826,13 +878,22 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="tsp20_b512", choices=sorted(WORKLOADS))
-    ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of --steps rollouts each; ms_per_step is the median block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-north-star", action="store_true")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps rollouts each; ms_per_step is the median block "
+                         "(default: 1, under --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: five timed blocks, rooflines, the other "
+                         "BASELINE configs, rates with env.reset(), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-north-star", action="store_true",
+                    help="with --full: skip the north-star / config-5 step rooflines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short runs of the other BASELINE configs")
+                    help="with --full: skip the short runs of the other BASELINE configs")
     a = ap.parse_args()
+    if a.blocks is None:
+        a.blocks = 5 if a.full else 1
 
     if a.gpus > 1 and "RANK" not in os.environ:
         spawn_ranks(a, sys.argv[1:])  # does not return
@@ -915,8 +976,14 @@ def rank_main(a, stage=None):
 
     kind, N, B, mode = WORKLOADS[a.workload]
     stage[0] = "timed workload " + a.workload
+    outputs = {} if a.dump_outputs and rank == 0 else None
     r, env, agent = run_workload(a.workload, a.steps, a.warmup, device, dist, rank, world,
-                                 blocks=max(a.blocks, 1))
+                                 blocks=max(a.blocks, 1), outputs=outputs)
+    dumped = None
+    if outputs is not None:
+        stage[0] = "dump outputs"
+        dumped = dump_outputs(outputs, a.dump_outputs)
+        outputs = None
     stage[0] = "report"
     T = r["T"]
     out = {
@@ -953,15 +1020,17 @@ def rank_main(a, stage=None):
         out["devices"] = idents
     if one_gpu and world > 1:
         out["one_gpu_test_mode"] = True  # all ranks share cuda:0: not a scaling measurement
+    if dumped is not None:
+        out["outputs"] = dumped
     if mode == "train":
         out["training"] = {k: r[k] for k in ("rollouts_per_step", "allreduce_ms_per_step",
                                              "grad_bucket_bytes")}
         out["roofline"] = r["roofline_train"]
-        if rank == 0:
+        if rank == 0 and a.full:
             out["roofline"]["dominant_kernel"] = gemm_kernel_roofline(device, B * N, 384, 128)
 
     # ---- short runs of the other BASELINE configs (bounded; failures are reported, not fatal)
-    if not a.no_extras and a.workload == "tsp20_b512":
+    if a.full and not a.no_extras and a.workload == "tsp20_b512":
         extras = {}
         todo = [("irp40_b1024_train", 6, 2)] if world > 1 else \
                [("vrp40_b2048_train", 6, 2), ("irp40_b1024_train", 6, 2), ("vrp100_b2048", 4, 1)]
@@ -973,7 +1042,7 @@ def rank_main(a, stage=None):
                 extras[name] = {"error": repr(exc)[:300]}
         out["other_configs"] = extras
 
-    if rank == 0 and mode != "train":
+    if rank == 0 and a.full and mode != "train":
         # `roofline` = the DOMINANT kernel of the benched rollout: whichever of the encoder
         # phase (fp32 MFMA-bound) and the decode/env step loop (HBM-bound) takes longer; both
         # are reported (roofline_encoder, roofline_step)
@@ -989,7 +1058,7 @@ def rank_main(a, stage=None):
             out["roofline_north_star_vrp"] = step_kernel_roofline(1, 40, 8192, True, device)
             if a.workload != "vrp100_b2048":
                 out["roofline_cfg5"] = step_kernel_roofline(1, 100, 2048, False, device, reps=2)
-    if rank == 0 and world == 1 and mode != "train":
+    if rank == 0 and a.full and world == 1 and mode != "train":
         # the same rollouts with env.reset() (new instances: host numpy stream + upload, or
         # the device generator) inside the timed region
         (dt,), T2, _ = timed_rollouts(env, agent, mode == "greedy", max(a.steps // 2, 1), 1, None,
@@ -1003,7 +1072,7 @@ def rank_main(a, stage=None):
         out["incl_env_reset_device_generator"] = {
             "ms_per_step": round(dt / a.steps * 1e3, 4),
             "value": round(a.steps * B * N * T2 / dt, 1)}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(kind, N, B, mode != "sample")
         if mode != "train":
             out["cpu_baseline"]["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)

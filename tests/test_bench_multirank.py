@@ -5,8 +5,8 @@ collectives run over gloo (VRPGYM_BENCH_ONE_GPU=1, flagged in the JSON line)."""
 import json
 import os
 import sys
-import warnings
 
+import numpy as np
 import pytest
 import torch
 
@@ -16,80 +16,31 @@ import _proc  # noqa: E402
 
 
 # Ranks that SHARE cuda:0 (the one-GPU test aid; never the product's deployment): about one
-# eight-rank start-up in sixty ends with "HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION" from the runtime's
-# queue-error callback.  Round 6 caught one under the ROCm debug agent (profiles/r06_crash_hunt.txt,
-# DESIGN.md 6.1): the four faulting waves belong to PyTorch's
-# `vectorized_elementwise_kernel<4, MulFunctor<float>>` (libtorch_hip.so, code object of 3 528 496
-# bytes) and were started AT that kernel's descriptor -- the descriptor read as zeros in device
-# memory, 8 s after the processes started, i.e. while HIP was still loading that code object lazily.
-# Not a kernel of this library, no scratch involved.  So these runs now ALWAYS run under the debug
-# agent, and the rule is about attribution, not about the error string: a run is started again --
-# once, recorded -- only if the agent's dump names a code object that is NOT one of
-# libvrpgym_hip.so's; an abort inside one of ours, an abort without a dump, a second abort, or any
-# other failure fails the test.
-SHARED_GPU_ABORT = "HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION"
-SHARED_GPU_RESTARTS = []   # (args, attribution) of every restart of this session
-DEBUG_AGENT = "/opt/rocm/lib/librocm-debug-agent.so.2"
-
-
-def _own_code_object_sizes():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    return {len(co) for co in kernel_resources.code_objects(kernel_resources.DEFAULT)}
-
-
-def foreign_fault(stderr, own_sizes):
-    """The debug agent's attribution of a queue-error abort: a description of the faulting code
-    object if every faulting wave sits in a code object that is not this library's, else None."""
-    import re
-    if SHARED_GPU_ABORT not in stderr:
-        return None
-    waves = re.findall(r"^wave_\d+: pc=(0x[0-9a-f]+).*reason: ILLEGAL_INSTRUCTION", stderr, re.M)
-    objs = re.findall(r"code object: (\S*?size=(\d+))", stderr)
-    if not waves or not objs:
-        return None                      # no dump: nothing to attribute, no restart
-    if any(int(size) in own_sizes for _, size in objs):
-        return None                      # a kernel of this library: a real failure
-    return "%d wave(s) at pc %s in foreign code object(s) of %s bytes" % (
-        len(waves), waves[0], sorted({int(size) for _, size in objs}))
+# eight-rank start-up in sixty ended with "HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION" in round 6, in a
+# kernel of PyTorch's, not of this library.  A run is started ONCE: whatever ends
+# it -- that abort included -- is the test's result, and nothing more is started on the GPU after
+# a fault.
 
 
 def _bench(args, extra_env=None, timeout=_proc.SUBPROCESS_TIMEOUT, env=None):
     """bench.py in a process group of its own that cannot outlive the test (tests/_proc.py; the
-    launcher inside bench.py gives its ranks the same property)."""
+    launcher inside bench.py gives its ranks the same property).  One run, never repeated."""
     if env is None:
         env = dict(os.environ)
     env.update(extra_env or {})
-    shared = env.get("VRPGYM_BENCH_ONE_GPU") == "1" and "--gpus" in args
-    if shared and os.path.exists(DEBUG_AGENT):
-        env.setdefault("HSA_TOOLS_LIB", DEBUG_AGENT)
-        env.setdefault("ROCM_DEBUG_AGENT_OPTIONS", "--all")
-    for attempt in range(2):
-        p = _proc.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, timeout=timeout)
-        if p.returncode == 0 or attempt or not shared:
-            break
-        who = foreign_fault(p.stderr, _own_code_object_sizes())
-        if who is None:
-            break
-        SHARED_GPU_RESTARTS.append((" ".join(args), who))
-        warnings.warn("ranks sharing cuda:0: a rank aborted in a kernel that is not this library's "
-                      "(%s); run started again once: %s" % (who, " ".join(args)))
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "shared_gpu_restarts.log"), "a") as fh:
-                fh.write(" ".join(args) + "\n" + who + "\n" + p.stderr[-6000:] + "\n")
-        except OSError:
-            pass
+    p = _proc.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, timeout=timeout)
     if p.returncode != 0:
-        # the tail of a torchrun failure is its summary table; keep the whole stream where a
-        # gpurun call brings it back, and put the lines that name the cause in front
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            tag = "_".join(a.strip("-") for a in args)[:80]
-            with open(os.path.join(ROOT, "gpurun_out", f"bench_stderr_{tag}.log"), "w") as fh:
-                fh.write(p.stderr)
-        except OSError:
-            pass
+        # the tail of a torchrun failure is its summary table; with VRPGYM_BENCH_LOG_DIR set the
+        # whole stream is kept there, and the lines that name the cause go in front
+        log_dir = os.environ.get("VRPGYM_BENCH_LOG_DIR")
+        if log_dir:
+            try:
+                os.makedirs(log_dir, exist_ok=True)
+                tag = "_".join(a.strip("-") for a in args)[:80]
+                with open(os.path.join(log_dir, f"bench_stderr_{tag}.log"), "w") as fh:
+                    fh.write(p.stderr)
+            except OSError:
+                pass
         cause = [l for l in p.stderr.splitlines()
                  if any(k in l for k in ("Error", "error", "HSA", "hip", "abort", "what():", "Assert"))
                  and "ChildFailedError" not in l][:30]
@@ -286,8 +237,60 @@ def test_bench_two_ranks_over_rccl(workload):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run: the headline only (one block of exactly --steps steps, no extra runs), and
+    --dump-outputs writes the last timed rollout's results -- the same in a second run."""
+    got = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        p = _bench(["--steps", "4", "--warmup", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[:4000]
+        out = _json_line(p.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 4 and out["value"] > 0 and out["ms_per_step"] > 0
+        for k in ("roofline", "other_configs", "cpu_baseline", "incl_env_reset", "dispersion"):
+            assert k not in out, k
+        # node-steps/s = B * N * T * steps / (steps * ms_per_step): one block of the 4 steps
+        T = out["config"]["steps_per_rollout"]
+        assert abs(out["value"] * out["ms_per_step"] / 1e3 / (512 * 20 * T) - 1) < 1e-2
+        assert sorted(os.listdir(d)) == ["acc_logp.npy", "acc_loss.npy", "emb.npy", "notdone.npy"]
+        arrs = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs["acc_loss"].shape == (512,) and arrs["emb"].shape == (512, 20, 128)
+        assert abs(-arrs["acc_loss"].mean() - out["mean_tour_cost"]) < 1e-4
+        assert out["outputs"]["emb"] == {"shape": [512, 20, 128], "sampled": None}
+        got.append(arrs)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
+def test_dump_outputs_writes_float32_within_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 files (float64 kept), 0-d results included, and an array above
+    its share of the budget written as a fixed, seeded, sorted sample of its elements."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(mod, "DUMP_BYTES", 3 * 4096)
+    big = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    outs = {"big": big, "ints": torch.arange(5, dtype=torch.int32), "loss": torch.tensor(2.5),
+            "f64": torch.ones(3, dtype=torch.float64)}
+    info = mod.dump_outputs(outs, str(tmp_path / "a"))
+    mod.dump_outputs(outs, str(tmp_path / "b"))
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert a["ints"].dtype == np.float32 and a["ints"].tolist() == [0, 1, 2, 3, 4]
+    assert a["loss"].dtype == np.float32 and float(a["loss"]) == 2.5
+    assert a["f64"].dtype == np.float64
+    assert info["big"] == {"shape": [100, 100], "sampled": 768} and a["big"].shape == (768,)
+    assert np.all(np.diff(a["big"]) >= 0) and np.all(a["big"] == np.floor(a["big"]))
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 3 * 4096
+
+
+@pytest.mark.gpu
 def test_bench_single_rank_line_has_contract_keys():
-    p = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-north-star"])
+    p = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-north-star", "--full"])
     assert p.returncode == 0, p.stderr[:4000]
     out = _json_line(p.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
@@ -319,25 +322,19 @@ def test_bench_single_rank_line_has_contract_keys():
         assert out["other_configs"][name]["ms_per_step"] > 0
 
 
-def test_shared_gpu_abort_restart_rule_is_about_attribution(monkeypatch, tmp_path):
-    """The one-GPU aid's restart rule: once, and only for a queue-error abort that
-    the debug agent's dump places in a code object that is not this library's; an abort in one of
-    ours, an abort without a dump, a second abort and every other failure are failures."""
+def test_failed_bench_run_is_never_started_again(monkeypatch, tmp_path):
+    """The one-GPU aid runs a bench ONCE: a queue-error abort of ranks that share
+    cuda:0 -- with or without a wave dump, in whichever code object -- and every other failure is
+    the test's result; no tool library is put into the ranks' environment; the stream of a failed
+    run lands in VRPGYM_BENCH_LOG_DIR when that is set."""
     class P:
         def __init__(self, rc, err):
             self.returncode, self.stderr, self.stdout = rc, err, ""
-    abort = ":0:rocdevice.cpp :3676: Callback: Queue 0x1 aborting with error : " + SHARED_GPU_ABORT
-
-    def dump(size):
-        return ("wave_4: pc=0x78c7ede49a00 (kernel_code_entry=0x78c7ede49a80) (stopped, reason: "
-                "ILLEGAL_INSTRUCTION)\nDisassembly:\n    code object: memory://1552#offset=0x64f5&size=%d\n"
-                % size + abort)
-    own = sorted(_own_code_object_sizes())
-    assert len(own) >= 10 and 3528496 not in own
-    assert foreign_fault(dump(3528496), set(own)) is not None      # PyTorch's: round 6's catch
-    assert foreign_fault(dump(own[-1]), set(own)) is None            # one of ours
-    assert foreign_fault(abort, set(own)) is None                    # no dump
-    assert foreign_fault("RuntimeError: x", set(own)) is None
+    abort = (":0:rocdevice.cpp :3676: Callback: Queue 0x1 aborting with error : "
+             "HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION")
+    dump = ("wave_4: pc=0x78c7ede49a00 (kernel_code_entry=0x78c7ede49a80) (stopped, reason: "
+            "ILLEGAL_INSTRUCTION)\nDisassembly:\n    code object: memory://1552#offset=0x64f5&"
+            "size=3528496\n" + abort)
     script = []
     calls = []
 
@@ -345,23 +342,23 @@ def test_shared_gpu_abort_restart_rule_is_about_attribution(monkeypatch, tmp_pat
         calls.append((cmd, dict(env or {})))
         return script.pop(0)
     monkeypatch.setattr(_proc, "run", fake_run)
+    monkeypatch.delenv("VRPGYM_BENCH_LOG_DIR", raising=False)
     one = {"VRPGYM_BENCH_ONE_GPU": "1"}
-    del SHARED_GPU_RESTARTS[:]
-    with pytest.warns(UserWarning, match="started again once"):
-        script[:] = [P(134, dump(3528496)), P(0, "")]
-        assert _bench(["--gpus", "8"], dict(one)).returncode == 0 and len(calls) == 2
-    assert len(SHARED_GPU_RESTARTS) == 1 and "3528496" in SHARED_GPU_RESTARTS[0][1]
-    if os.path.exists(DEBUG_AGENT):      # ranks that share a GPU always run under the agent
-        assert calls[0][1].get("HSA_TOOLS_LIB") == DEBUG_AGENT
-    with pytest.warns(UserWarning):
-        script[:] = [P(134, dump(3528496)), P(134, dump(3528496))]
-        assert _bench(["--gpus", "8"], dict(one)).returncode == 134 and len(calls) == 4
-    script[:] = [P(134, dump(own[0]))]    # a kernel of this library: no second chance
-    assert _bench(["--gpus", "8"], dict(one)).returncode == 134 and len(calls) == 5
-    script[:] = [P(134, abort)]           # the bare abort, nothing to attribute it with
-    assert _bench(["--gpus", "8"], dict(one)).returncode == 134 and len(calls) == 6
-    script[:] = [P(1, "RuntimeError: something else")]
-    assert _bench(["--gpus", "8"], dict(one)).returncode == 1 and len(calls) == 7
-    script[:] = [P(134, dump(3528496))]   # one process per GPU: never restarted
+    for rc, err in ((134, dump), (134, abort), (-6, abort), (139, "Segmentation fault"),
+                    (1, "RuntimeError: something else")):
+        n = len(calls)
+        script[:] = [P(rc, err), P(0, "")]   # a second run would succeed: it must not happen
+        p = _bench(["--gpus", "8"], dict(one))
+        assert p.returncode == rc and len(calls) == n + 1 and len(script) == 1, (rc, err)
+        assert err.splitlines()[-1] in p.stderr
+        assert calls[-1][1].get("HSA_TOOLS_LIB") == os.environ.get("HSA_TOOLS_LIB")
     env = {k: v for k, v in os.environ.items() if k != "VRPGYM_BENCH_ONE_GPU"}
-    assert _bench(["--gpus", "8"], env=env).returncode == 134 and len(calls) == 8
+    script[:] = [P(134, dump), P(0, "")]    # one process per GPU: the same
+    assert _bench(["--gpus", "8"], env=env).returncode == 134 and len(calls) == 6
+    script[:] = [P(0, "")]
+    assert _bench(["--steps", "3"]).returncode == 0 and len(calls) == 7
+    assert not os.listdir(tmp_path)
+    monkeypatch.setenv("VRPGYM_BENCH_LOG_DIR", str(tmp_path / "logs"))
+    script[:] = [P(134, dump)]
+    assert _bench(["--gpus", "8"], dict(one)).returncode == 134 and len(calls) == 8
+    assert open(tmp_path / "logs" / "bench_stderr_gpus_8.log").read() == dump

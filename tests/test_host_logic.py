@@ -378,7 +378,9 @@ def test_host_side_under_sanitizers():
                         capture_output=True, text=True).stdout.strip()
     assert os.path.exists(rt), rt
     env = dict(os.environ)
-    env.update(LD_PRELOAD=rt, VRPGYM_HIP_LIB=os.path.join(ROOT, "vrp-gym_amd", "vrpgym_hip",
+    # the ASan runtime goes first; whatever the environment already preloads stays preloaded
+    preload = ":".join(p for p in (rt, os.environ.get("LD_PRELOAD", "")) if p)
+    env.update(LD_PRELOAD=preload, VRPGYM_HIP_LIB=os.path.join(ROOT, "vrp-gym_amd", "vrpgym_hip",
                                                          "libvrpgym_hip_asan.so"),
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
