@@ -166,7 +166,8 @@ int vrp_encoder_forward_from_env(const vrp_encoder_weights *w, int train, const 
                                  float *dec_cvec, unsigned long long *dec_hist, int32_t *dec_err,
                                  const float *dec_warm, int dec_warm_floats,
                                  const float *dec_wqgT, const float *dec_bq, float *dec_QG,
-                                 int *decoder_constants_done, hipStream_t st);
+                                 const StackTables *dec_tables, int *decoder_constants_done,
+                                 hipStream_t st);
 int vrp_decode_prologue_ex(int kind, const void *derived, int B, int N, const float *emb,
                            void *workspace, int constants_done, void *stream);
 
@@ -178,7 +179,7 @@ int vrp_decode_prologue_ex(int kind, const void *derived, int B, int N, const fl
 static int rollout_encode(int kind, const vrp_encoder_weights *ew, void *derived,
                           const vrp_env *env, int train, float *emb, void *enc_workspace,
                           void *dec_workspace, const vrp_rollout_io *io, int max_steps,
-                          int *constants_done, void *stream) {
+                          bool tables, int *constants_done, void *stream) {
   VRP_REQUIRE(ew && derived && env && emb && enc_workspace && dec_workspace && io,
               "rollout: NULL argument");
   VRP_REQUIRE(io->acc_loss && io->acc_logp && io->notdone, "rollout: io accumulators NULL");
@@ -191,10 +192,17 @@ static int rollout_encode(int kind, const vrp_encoder_weights *ew, void *derived
   VRP_REQUIRE(max_steps >= need, "rollout: max_steps=%d < %d", max_steps, need);
   Derived d = carve_derived(derived);
   DecWs w = carve_decws(dec_workspace, B, N);
+  // what the decoder prologue would write, for the stack kernel's tables tail (the encoder decides
+  // whether it runs: constants_done bit 2)
+  StackTables tb;
+  tb.kind = kind; tb.Wproj = d.WprojS; tb.bproj = d.bproj; tb.qc0 = d.qc0; tb.wload = d.wload;
+  tb.SG = w.SG; tb.C0 = w.C0; tb.SLD = w.SLD; tb.row0 = w.row0; tb.SL = w.SL; tb.RT = w.RT;
+  tb.KK4 = kind != VRP_KIND_IRP ? w.KK4 : nullptr;
   return vrp_encoder_forward_from_env(ew, train, env, emb, enc_workspace, io->acc_loss,
                                       io->acc_logp, io->notdone, max_steps + 1, d.mb, w.g, w.cvec,
                                       w.hist, w.err, use_fused_prologue(N) ? d.Wproj : nullptr,
-                                      1536 * 128, d.WqgT, d.bq, w.QG, constants_done,
+                                      1536 * 128, d.WqgT, d.bq, w.QG,
+                                      tables && use_fused_prologue(N) ? &tb : nullptr, constants_done,
                                       (hipStream_t)stream);
 }
 
@@ -203,8 +211,9 @@ extern "C" int vrp_rollout_encode(int kind, const vrp_encoder_weights *ew, void 
                                   void *dec_workspace, const vrp_rollout_io *io, int max_steps,
                                   void *stream) {
   int constants_done = 0;
+  // (the encoder phase alone: its callers run the whole prologue afterwards)
   return rollout_encode(kind, ew, derived, env, train, emb, enc_workspace, dec_workspace, io,
-                        max_steps, &constants_done, stream);
+                        max_steps, false, &constants_done, stream);
 }
 
 extern "C" int vrp_rollout(int kind, const vrp_encoder_weights *ew, const vrp_decoder_weights *dw,
@@ -214,7 +223,7 @@ extern "C" int vrp_rollout(int kind, const vrp_encoder_weights *ew, const vrp_de
   VRP_REQUIRE(dw, "rollout: NULL argument");
   int constants_done = 0;
   if (int r = rollout_encode(kind, ew, derived, env, train, emb, enc_workspace, dec_workspace, io,
-                             max_steps, &constants_done, stream)) return r;
+                             max_steps, true, &constants_done, stream)) return r;
   const int B = env->B, N = env->N;
   if (int r = vrp_decode_prologue_ex(kind, derived, B, N, emb, dec_workspace, constants_done,
                                      stream)) return r;

@@ -115,16 +115,18 @@ __global__ __launch_bounds__(256) void pack_fold_weights_kernel(const float *__r
 }
 
 // Wproj = [Wq_last | Wk | M^T | Wv] (1536,128) as three bf16 planes in the fragment order of the
-// fused prologue's stage 1 (decoder_ws.h: WprojX3).  One thread per (fragment, chunk, lane).
+// fused prologue's stage 1 (decoder_ws.h: WprojX3), or (stack = 1) in the k order and fragment
+// order of the x3 stack kernel's tables tail (WprojS).  One thread per (fragment, chunk, lane).
 __global__ __launch_bounds__(256) void pack_proj_x3_kernel(const float *__restrict__ Wproj,
-                                                           __bf16 *__restrict__ out) {
+                                                           __bf16 *__restrict__ out, int stack) {
   const int idx = blockIdx.x * 256 + threadIdx.x;   // 96 fragments x 4 chunks x 64 lanes
   if (idx >= 96 * 256) return;
   const int lane = idx & 63, j = (idx >> 6) & 3, f = idx >> 8;
-  const int c = f % 3, X = (f / 3) & 3, h = f / 12;
+  const int c = f % 3, X = (f / 3) & 3;
+  const int h = stack ? 2 * (f / 24) + (f / 12) % 2 : f / 12;
   const int j16 = lane & 15, q = lane >> 4;
-  const float *src = Wproj + (size_t)(X * 384 + h * VRP_HD + 16 * c + j16) * VRP_EMB +
-                     64 * (q & 1) + 32 * (q >> 1) + 8 * j;
+  const int k0 = stack ? 32 * j + 8 * q : 64 * (q & 1) + 32 * (q >> 1) + 8 * j;
+  const float *src = Wproj + (size_t)(X * 384 + h * VRP_HD + 16 * c + j16) * VRP_EMB + k0;
   bf16x8 hp, mp, lp;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -202,7 +204,10 @@ extern "C" int vrp_decoder_prepare(int kind, const vrp_decoder_weights *w, void 
                      d.Wproj + (size_t)1152 * 128, d.M, d.WvP, d.MP);
   VRP_CHECK_LAUNCH("pack_fold_weights");
   hipLaunchKernelGGL(pack_proj_x3_kernel, dim3(96), dim3(256), 0, st, d.Wproj,
-                     reinterpret_cast<__bf16 *>(d.WprojX3));
+                     reinterpret_cast<__bf16 *>(d.WprojX3), 0);
+  VRP_CHECK_LAUNCH("pack_proj_x3");
+  hipLaunchKernelGGL(pack_proj_x3_kernel, dim3(96), dim3(256), 0, st, d.Wproj,
+                     reinterpret_cast<__bf16 *>(d.WprojS), 1);
   VRP_CHECK_LAUNCH("pack_proj_x3");
   return 0;
 }

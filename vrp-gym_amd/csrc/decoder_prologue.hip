@@ -989,7 +989,8 @@ extern "C" int vrp_decode_prologue(int kind, const void *derived, int B, int N, 
 }
 
 // constants_done: bit 0: the graph mean, cvec and the cleared hand-off words were already produced
-// by the encoder's stack kernel (vrp_rollout, small batches); bit 1: QG as well
+// by the encoder's stack kernel (vrp_rollout, small batches); bit 1: QG as well; bit 2: the
+// tables, extra rows and keys too (encoder_stack_tables_x3_kernel)
 int vrp_decode_prologue_ex(int kind, const void *derived, int B, int N, const float *emb,
                            void *workspace, int constants_done, void *stream) {
   VRP_REQUIRE(derived && emb && workspace, "decode_prologue: NULL argument");
@@ -1006,7 +1007,9 @@ int vrp_decode_prologue_ex(int kind, const void *derived, int B, int N, const fl
   if (!(constants_done & 2))   // (the x3 stack kernel's epilogue leaves QG too)
     if (int r = vrp_launch_gemm_nt(w.g, 128, d.Wqg, 128, d.bq, nullptr, 0, w.QG, 384, B, 384, 128, 0,
                                    st)) return r;
-  if (use_fused_prologue(N)) {
+  if (constants_done & 4) {
+    // (written by the stack kernel's tail)
+  } else if (use_fused_prologue(N)) {
     const PrologueParams p = prologue_params(kind, B, N, emb, d, w);
     if (int r = (N & 3) == 0 ? launch_prologue_vec<true>(p, st) : launch_prologue_vec<false>(p, st))
       return r;

@@ -35,6 +35,10 @@ struct Derived {
                    // for its own graphs, lane = output column (coalesced), instead of a GEMM launch
   float *WqfT;     // (128,384)  Wqf transposed: the persistent kernels project the first chosen node
                    // themselves (decoder_persistent.hip: persist_first_base)
+  float *WprojS;   // Wproj as bf16-plane fragments in the x3 STACK kernel's order (encoder_x3.h: lane
+                   // (j16, q), chunk j holds k = 32 j + 8 q .. + 7): fragment 24 P + 12 hh + 3 X + c =
+                   // rows X*384 + 48 (2 P + hh) + 16 c + j16 -- pass P of the stack kernel's tables tail
+                   // covers heads 2 P, 2 P + 1 (encoder.hip: stack_tables_pass)
 };
 
 static inline Derived carve_derived(void *base) {
@@ -60,13 +64,14 @@ static inline Derived carve_derived(void *base) {
   d.WprojX3 = p; p += VRP_WPROJ_X3_FLOATS;
   d.WqgT = p;  p += 128 * 384;
   d.WqfT = p;  p += 128 * 384;
+  d.WprojS = p; p += VRP_WPROJ_X3_FLOATS;
   return d;
 }
 
 static inline int64_t derived_floats() {
   return 1536 * 128 + 1536 + 384 * 128 + 384 * 128 + 384 * 3 + 128 * 384 + 384 + 384 * 128 + 128 +
          128 * 384 + 128 + 128 * 384 + 1024 * 128 + 384 * 128 + 128 * 384 + VRP_WPROJ_X3_FLOATS +
-         128 * 384 + 128 * 384;
+         128 * 384 + 128 * 384 + VRP_WPROJ_X3_FLOATS;
 }
 
 // ------------------------------------------------------------------ per-episode workspace
@@ -220,6 +225,17 @@ static inline int64_t decws_bytes(int B, int N) {
                    vrp_align_up((size_t)hist_rows(N) * B * 8) + vrp_align_up(4) +
                    persist_save_bytes(B, N));
 }
+
+// The decoder prologue's tables written by the x3 encoder stack kernel itself (encoder.hip:
+// encoder_stack_tables_x3_kernel, vrp_rollout on small batches): what prologue_tables_kernel
+// reads and writes, in the same DecWs layouts.
+struct StackTables {
+  int kind;
+  const void *Wproj;                       // Derived::WprojS (bf16 fragments, stack k order)
+  const float *bproj, *qc0, *wload;        // Derived
+  float *SG, *C0, *SLD, *row0, *SL, *RT;   // DecWs
+  float *KK4;                              // DecWs::KK4 or NULL (IRP, or keys not kept)
+};
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

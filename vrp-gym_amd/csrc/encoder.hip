@@ -5,6 +5,7 @@
 // attention, the batch statistics and the normalisation are small HBM-bound kernels.
 #include <stdlib.h>
 #include "env_device.h"
+#include "decoder_ws.h"
 
 int vrp_launch_gemm_nt(const float *A, int lda, const float *W, int ldw, const float *bias,
                        const float *R, int ldr, float *C, int ldc, int M, int N, int K,
@@ -2623,6 +2624,154 @@ static int launch_encoder_stack(const vrp_encoder_weights *w, const float *x, co
   return 0;
 }
 
+// ---- the decoder prologue's tables as the x3 stack kernel's tail (encoder_stack_tables_x3_kernel) ----
+// At the end of the last layer the workgroup holds its graphs' final embeddings as bf16 planes in
+// XB3 -- exactly the A operand prologue_tables_kernel builds for the same pack of graphs -- and
+// QG in memory.  Four passes, two heads each:
+//   stage 1: [QL | KK | KM | VV] of the pass's two heads (384 columns) = three x3_mma stages of
+//            eight waves x 16 columns (Derived::WprojS, fragment 8 s + wave of the pass; the
+//            fragment of the next stage travels under each stage, the first one under the last
+//            layer's final stage), + bias, fp32 into Q_s;
+//   stage 2: per (head, graph) the N x N tables SL = QL KK^T / sqrt(48) (IRP: + SG) and
+//            RT = KM VV^T, the extra rows SG, C0, SLD, row0, and the glimpse keys KK4, on the VALU
+//            from Q_s: a thread owns a 4 x 4 block of a table (two k-parity chains per element,
+//            v_pk_fma_f32) or one node's extra rows.  Same DecWs layouts as the prologue.
+__device__ __forceinline__ void st_dot4(x3_f32x2 &acc, const float4 &a, const float4 &b) {
+  acc = __builtin_elementwise_fma(x3_f32x2{a.x, a.y}, x3_f32x2{b.x, b.y}, acc);
+  acc = __builtin_elementwise_fma(x3_f32x2{a.z, a.w}, x3_f32x2{b.z, b.w}, acc);
+}
+template <int RT16>
+__device__ __forceinline__ void stack_tables_tail(const StackTables &tb, const float *__restrict__ QG,
+                                                  int g0, const __bf16 *XB3, int PE, float *Q_s,
+                                                  Frag3 &fa, Frag3 &fb, int N, int graphs, int tid) {
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i16 = lane & 15, q = lane >> 4;
+  const __bf16 *wf = reinterpret_cast<const __bf16 *>(tb.Wproj);
+  const float c48 = 0.14433756729740643f;   // 1/sqrt(48)
+  const bool fold = tb.kind == VRP_KIND_IRP;
+  const int Nb = (N + 3) >> 2, nx = 2 * graphs * N, nt = 4 * graphs * Nb * Nb;
+  f32x4v acc[RT16];
+  // stage s of pass P reads `cur`, `nxt` receives the next stage's fragment (the last stage of
+  // pass 3 requests its own again: no branch inside the MFMA sequence)
+  auto proj = [&](int P, int s, const Frag3 &cur, Frag3 &nxt) {
+    const int t = 3 * P + s, tn = t + 1 < 12 ? t + 1 : t;
+    const int f = 8 * s + wave, hh = f / 12, X = (f % 12) / 3, c = f % 3;
+#pragma unroll
+    for (int rt = 0; rt < RT16; ++rt) acc[rt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    x3_mma<RT16>(acc, XB3, PE, cur, lane, X3FragStream(nxt, wf + (size_t)(8 * tn + wave) * X3_FRAG, lane));
+    const float4 bb = x3_ld4(tb.bproj + X * 384 + (2 * P + hh) * 48 + 16 * c + 4 * q);
+    const int col0 = 16 * f + 4 * q;   // = 192 hh + 48 X + 16 c + 4 q
+#pragma unroll
+    for (int rt = 0; rt < RT16; ++rt)
+      *reinterpret_cast<float4 *>(Q_s + (rt * 16 + i16) * QA_QLD + col0) =
+          make_float4(acc[rt][0] + bb.x, acc[rt][1] + bb.y, acc[rt][2] + bb.z, acc[rt][3] + bb.w);
+  };
+  auto tables = [&](int P) {
+    for (int u = tid; u < nx + nt; u += 512) {
+      if (u < nx) {
+        // ---- extra rows of node n: [QG ; qc0 ; wload]_h . KK_n / sqrt(48), and the keys ----
+        const int n = u % N, g = (u / N) % graphs, hh = u / (N * graphs), h = 2 * P + hh, b = g0 + g;
+        const float *kk = Q_s + (g * N + n) * QA_QLD + 192 * hh + 48;
+        const float *qg = QG + (size_t)b * VRP_D + h * VRP_HD;
+        x3_f32x2 s0 = {0.f, 0.f}, s1 = s0, s2 = s0;
+#pragma unroll
+        for (int k = 0; k < 48; k += 4) {
+          const float4 kv = x3_ld4(kk + k);
+          st_dot4(s0, x3_ld4(qg + k), kv);
+          st_dot4(s1, x3_ld4(tb.qc0 + h * VRP_HD + k), kv);
+          st_dot4(s2, x3_ld4(tb.wload + h * VRP_HD + k), kv);
+        }
+        const float sg = (s0.x + s0.y) * c48, c0 = (s1.x + s1.y) * c48;
+        const size_t o = ((size_t)b * 8 + h) * N + n;
+        tb.SG[o] = sg;
+        tb.C0[o] = c0;
+        tb.SLD[o] = (s2.x + s2.y) * c48;
+        tb.row0[o] = sg + c0;   // the step-0 score row
+        if (tb.KK4) {           // (B,8,12,N,4): columns 4 c4 .. + 3 of node n
+          float4 *dst = reinterpret_cast<float4 *>(tb.KK4) + (((size_t)b * 8 + h) * 12) * N + n;
+#pragma unroll
+          for (int c4 = 0; c4 < 12; ++c4) dst[(size_t)c4 * N] = x3_ld4(kk + 4 * c4);
+        }
+        continue;
+      }
+      // ---- a 4 x 4 block of SL (T = 0) or RT (T = 1): rows m = 4 mb + i, columns n = 4 nb + j ----
+      int r = u - nx;
+      const int nb = r % Nb; r /= Nb;
+      const int mb = r % Nb; r /= Nb;
+      const int g = r % graphs; r /= graphs;
+      const int hh = r & 1, T = r >> 1, h = 2 * P + hh, b = g0 + g;
+      const float *qa = Q_s + 192 * hh + (T ? 96 : 0);    // QL | KM
+      const float *qb = Q_s + 192 * hh + (T ? 144 : 48);  // KK | VV
+      int ra[4], rb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {   // (rows beyond the graph read its last row: never stored)
+        ra[i] = (g * N + min(4 * mb + i, N - 1)) * QA_QLD;
+        rb[i] = (g * N + min(4 * nb + i, N - 1)) * QA_QLD;
+      }
+      const float *qg = QG + (size_t)b * VRP_D + h * VRP_HD;
+      x3_f32x2 a2[4][4], sgc[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        sgc[i] = x3_f32x2{0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a2[i][j] = x3_f32x2{0.f, 0.f};
+      }
+#pragma unroll 2
+      for (int k = 0; k < 48; k += 4) {
+        float4 av[4], bv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { av[i] = x3_ld4(qa + ra[i] + k); bv[i] = x3_ld4(qb + rb[i] + k); }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) st_dot4(a2[i][j], av[i], bv[j]);
+        if (fold && T == 0) {   // IRP: SG of the block's columns, as the extra rows compute it
+          const float4 gv = x3_ld4(qg + k);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) st_dot4(sgc[j], gv, bv[j]);
+        }
+      }
+      float bcol[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bcol[j] = (fold && T == 0) ? (sgc[j].x + sgc[j].y) * c48 : 0.f;
+      const float scale = T ? 1.f : c48;
+      float *tab = T ? tb.RT : tb.SL;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = 4 * mb + i;
+        if (m >= N) continue;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaf(a2[i][j].x + a2[i][j].y, scale, bcol[j]);
+        float *dst = tab + (((size_t)b * N + m) * 8 + h) * N + 4 * nb;
+        if ((N & 3) == 0) {
+          *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (4 * nb + j < N) dst[j] = v[j];
+        }
+      }
+    }
+  };
+  // buffer roles: pass 2 p2 reads fa, fb, fa; pass 2 p2 + 1 fb, fa, fb (the last layer's final
+  // stage left the first fragment in fa)
+  for (int p2 = 0; p2 < 2; ++p2) {
+    proj(2 * p2, 0, fa, fb);
+    proj(2 * p2, 1, fb, fa);
+    proj(2 * p2, 2, fa, fb);
+    __syncthreads();
+    tables(2 * p2);
+    __syncthreads();
+    proj(2 * p2 + 1, 0, fb, fa);
+    proj(2 * p2 + 1, 1, fa, fb);
+    proj(2 * p2 + 1, 2, fb, fa);
+    __syncthreads();
+    tables(2 * p2 + 1);
+    __syncthreads();
+  }
+}
+
 // ---- the stack kernel on the bf16 matrix cores (round 5; encoder_x3.h) -----------------------
 // Same decomposition -- G whole graphs per workgroup through all layers, eight waves, a wave owns
 // 16 output columns of the block stages, one 48-column block of in_proj and one attention head --
@@ -2636,12 +2785,16 @@ static int launch_encoder_stack(const vrp_encoder_weights *w, const float *x, co
 //     the fragment of stage i + 1 is requested when stage i starts;
 //   * the attention itself (K = 16 per head) stays on the fp32 MFMA, q|k|v in fp32.
 // Stage order per layer: P0 P1 P2 | attention | O | U0 | (D0 U1) (D1 U2) (D2 U3) | D3.
-template <int RT16>
-__global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weights w,
-                                                                const float *__restrict__ x,
-                                                                const float *__restrict__ norms_in,
-                                                                float *__restrict__ y, int B, int N,
-                                                                int G, StackSetup su, StackEpilogue ep) {
+// The body is shared by two kernels: encoder_stack_x3_kernel (TABLES = false) and
+// encoder_stack_tables_x3_kernel (TABLES = true: the decoder prologue's tables as a tail, see
+// stack_tables_tail above).
+template <int RT16, bool TABLES>
+__device__ __forceinline__ void encoder_stack_x3_body(const vrp_encoder_weights &w,
+                                                      const float *__restrict__ x,
+                                                      const float *__restrict__ norms_in,
+                                                      float *__restrict__ y, int B, int N, int G,
+                                                      const StackSetup &su, const StackEpilogue &ep,
+                                                      const StackTables &tb) {
   constexpr int RTW = 16 * RT16, PE = RTW * X3_PITCH;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __bf16 *XB3 = reinterpret_cast<__bf16 *>(smem);    // [3][RTW][X3_PITCH]  layer input, then y1
@@ -2876,9 +3029,12 @@ __global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weigh
                    mult = x3_ld4(n2 + 128 + cq), beta = x3_ld4(n2 + 256 + cq);
       // (hidden >= 256: see the loop)  The next layer's first in_proj fragment travels under it
       // (the last layer requests its own first fragment again: twelve loads nobody uses, cheaper
-      // than a branch inside the MFMA sequence)
+      // than a branch inside the MFMA sequence -- or, with the tables tail, the first fragment of
+      // the decoder's projections)
+      const __bf16 *last_next = TABLES ? reinterpret_cast<const __bf16 *>(tb.Wproj) + (size_t)wave * X3_FRAG : lf;
       x3_mma<RT16>(gacc, ((nchunk - 1) & 1) ? H1 : AT3, PE, B, lane,
-                   X3FragStream(A, lf + (size_t)(l + 1 < w.num_layers ? per_layer + x3_frag_win(wave * 3) : 0) * X3_FRAG, lane));
+                   X3FragStream(A, l + 1 < w.num_layers ? lf + (size_t)(per_layer + x3_frag_win(wave * 3)) * X3_FRAG
+                                                        : last_next, lane));
       ST_MARK(4 + 24 * l + 21);
       // ---- y = BN2(y1 + g + b2): the next layer's input ----------------------------------------
 #pragma unroll
@@ -2887,7 +3043,7 @@ __global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weigh
         xres[rt].y = (gacc[rt][1] + bb.y + xres[rt].y - mean.y) * mult.y + beta.y;
         xres[rt].z = (gacc[rt][2] + bb.z + xres[rt].z - mean.z) * mult.z + beta.z;
         xres[rt].w = (gacc[rt][3] + bb.w + xres[rt].w - mean.w) * mult.w + beta.w;
-        if (l + 1 < w.num_layers) x3_store4v(XB3, PE, rt * 16 + i16, cq, xres[rt]);
+        if (TABLES || l + 1 < w.num_layers) x3_store4v(XB3, PE, rt * 16 + i16, cq, xres[rt]);   // (tables: stage 1's operand)
       }
     }
     ST_MARK(4 + 24 * l + 23);
@@ -2907,7 +3063,9 @@ __global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weigh
         *reinterpret_cast<const float4 *>(stage + r * EB_LD + c4);
   }
   if (ep.g) {
-    float *gs = reinterpret_cast<float *>(XB3);   // [graphs][128]: the means once more, for QG below
+    // [graphs][128]: the means once more, for QG below -- in AT3 (free after the last layer; XB3
+    // keeps the final embeddings' planes for the tables tail): at most 48 x 128 of its 9216 floats
+    float *gs = reinterpret_cast<float *>(AT3);
     for (int i = tid; i < graphs * 128; i += 512) {
       const int g = i >> 7, cc = i & 127;
       float s = 0.f;
@@ -2928,7 +3086,9 @@ __global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weigh
     if (blockIdx.x == 0 && tid == 0) *ep.err = 0;
     if (ep.QG) {   // (workgroup-uniform)
       __syncthreads();
-      stack_epilogue_qg(ep, gs, gs + 16 * 128, g0, graphs, tid);   // (XB3's 36 KB: means, then 24 KB of partials)
+      // (the 24 KB of partials in the fp32 staging rows, read by nobody after the barrier: they
+      // used to sit at gs + 16 x 128, over the means of graphs >= 16 when N <= 2)
+      stack_epilogue_qg(ep, gs, stage, g0, graphs, tid);
     }
     if (ep.warm) {
       const int per_xcd = (gridDim.x + 7) >> 3, slot = blockIdx.x >> 3;
@@ -2938,8 +3098,26 @@ __global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weigh
       if (sink == 1.2345678e-30f) y[0] = sink;   // never true: the loads must not be elided
     }
   }
+  if constexpr (TABLES) stack_tables_tail<RT16>(tb, ep.QG, g0, XB3, PE, Q_s, fa, fb, N, graphs, tid);
   ST_MARK(ST_SLOTS - 2);
   ST_MARK(ST_SLOTS - 1);
+}
+template <int RT16>
+__global__ __launch_bounds__(512) void encoder_stack_x3_kernel(vrp_encoder_weights w,
+                                                                const float *__restrict__ x,
+                                                                const float *__restrict__ norms_in,
+                                                                float *__restrict__ y, int B, int N,
+                                                                int G, StackSetup su, StackEpilogue ep) {
+  encoder_stack_x3_body<RT16, false>(w, x, norms_in, y, B, N, G, su, ep, StackTables{});
+}
+// ... and with the decoder prologue's tables as its tail (vrp_rollout, stack_tables_applies):
+// replaces the prologue_tables_kernel launch that would follow
+template <int RT16>
+__global__ __launch_bounds__(512) void encoder_stack_tables_x3_kernel(vrp_encoder_weights w,
+                                                                       float *__restrict__ y, int B, int N,
+                                                                       int G, StackSetup su, StackEpilogue ep,
+                                                                       StackTables tb) {
+  encoder_stack_x3_body<RT16, true>(w, nullptr, nullptr, y, B, N, G, su, ep, tb);
 }
 
 // the x3 stack kernel: pre-split weights present, at most five layers (LDS: 2 x 36 KB of operand
@@ -2953,22 +3131,29 @@ static bool encoder_x3_rows_ok(long rows) { return rows * 128 < (1l << 31); }
 template <int RT16>
 static int launch_encoder_stack_x3(const vrp_encoder_weights *w, const float *x, const float *norms,
                                    float *y, int B, int N, const StackSetup &su,
-                                   const StackEpilogue &ep, hipStream_t st) {
+                                   const StackEpilogue &ep, const StackTables *tb, hipStream_t st) {
   constexpr int RTW = 16 * RT16;
   const size_t lds = (size_t)2 * 3 * RTW * X3_PITCH * 2 + (size_t)RTW * QA_QLD * 4 +
                      (size_t)2 * w->num_layers * 384 * 4;
-  static VrpAttrOnce attr_set;
-  if (!attr_set.done()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&encoder_stack_x3_kernel<RT16>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+  static VrpAttrOnce attr_set, attr_set_tables;
+  VrpAttrOnce &as = tb ? attr_set_tables : attr_set;
+  if (!as.done()) {
+    const void *k = tb ? reinterpret_cast<const void *>(&encoder_stack_tables_x3_kernel<RT16>)
+                       : reinterpret_cast<const void *>(&encoder_stack_x3_kernel<RT16>);
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       vrp_set_error("encoder_stack_x3: cannot raise dynamic LDS to 160 KB");
       return 1;
     }
-    attr_set.mark();
+    as.mark();
   }
   const int G = RTW / N;
-  hipLaunchKernelGGL(encoder_stack_x3_kernel<RT16>, dim3((B + G - 1) / G), dim3(512), lds, st, *w, x,
-                     norms, y, B, N, G, su, ep);
+  if (tb) {   // (from the environment only: vrp_rollout)
+    hipLaunchKernelGGL(encoder_stack_tables_x3_kernel<RT16>, dim3((B + G - 1) / G), dim3(512), lds, st,
+                       *w, y, B, N, G, su, ep, *tb);
+  } else {
+    hipLaunchKernelGGL(encoder_stack_x3_kernel<RT16>, dim3((B + G - 1) / G), dim3(512), lds, st, *w, x,
+                       norms, y, B, N, G, su, ep);
+  }
   VRP_CHECK_LAUNCH("encoder_stack_x3");
 #ifdef VRP_STACK_TRACE
   stack_trace_dump();
@@ -2977,6 +3162,31 @@ static int launch_encoder_stack_x3(const vrp_encoder_weights *w, const float *x,
 }
 static bool encoder_stack_x3_applies(const vrp_encoder_weights *w) {
   return encoder_x3_enabled(w) && w->num_layers <= 5 && w->hidden >= 256;
+}
+// The decoder prologue's tables inside the x3 stack kernel (encoder_stack_tables_x3_kernel), for
+// vrp_rollout on the shapes where the standalone prologue would take its bf16-plane instance and
+// the stack kernel's grid has at least one workgroup per CU: on smaller grids the tail runs the
+// eight heads of a workgroup one pass after another on fewer CUs than the prologue's (pack, head)
+// units would spread over.  VRP_STACK_NO_TABLES=1: the standalone prologue (A/B aid).
+static bool encoder_stack_applies(const vrp_encoder_weights *w, int train, int B, int N);
+static bool stack_tables_applies(const vrp_encoder_weights *w, int train, int B, int N) {
+  static const bool off = getenv("VRP_STACK_NO_TABLES") != nullptr ||
+                          getenv("VRP_PROLOGUE_FP32") != nullptr;
+  if (off || !encoder_stack_applies(w, train, B, N) || !encoder_stack_x3_applies(w) ||
+      !use_fused_prologue(N))
+    return false;
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      n = 256;
+    }
+    cus = n;
+  }
+  const int G = 48 / N;
+  return (B + G - 1) / G >= cus;
 }
 
 // ---- out-proj + BN1 + FF + BN2 for LARGE row counts on the bf16 matrix cores -----------------
@@ -3574,7 +3784,8 @@ int vrp_encoder_forward_from_env(const vrp_encoder_weights *w, int train, const 
                                  float *dec_cvec, unsigned long long *dec_hist, int32_t *dec_err,
                                  const float *dec_warm, int dec_warm_floats,
                                  const float *dec_wqgT, const float *dec_bq, float *dec_QG,
-                                 int *decoder_constants_done, hipStream_t st) {
+                                 const StackTables *dec_tables, int *decoder_constants_done,
+                                 hipStream_t st) {
   const int B = env->B, N = env->N;
   if (int r = encoder_check(w, B, N)) return r;
   VRP_REQUIRE(env->kind == VRP_KIND_TSP || w->depot_embed_weight,
@@ -3597,7 +3808,12 @@ int vrp_encoder_forward_from_env(const vrp_encoder_weights *w, int train, const 
         ep.wqgT = dec_wqgT; ep.bq = dec_bq; ep.QG = dec_QG;
         *decoder_constants_done |= 2;             // bit 1: QG = Wq_g g + bq
       }
-      return launch_encoder_stack_x3<3>(w, nullptr, nullptr, emb, B, N, su, ep, st);
+      const bool tables = ep.QG && dec_tables && stack_tables_applies(w, train, B, N);
+      if (tables) {
+        ep.warm = nullptr;                        // (nobody reads the prologue's weights afterwards)
+        *decoder_constants_done |= 4;             // bit 2: tables, extra rows and keys
+      }
+      return launch_encoder_stack_x3<3>(w, nullptr, nullptr, emb, B, N, su, ep, tables ? dec_tables : nullptr, st);
     }
     return launch_encoder_stack<3>(w, nullptr, nullptr, emb, B, N, su, ep, st);
   }
@@ -3613,6 +3829,8 @@ int vrp_encoder_forward_from_env(const vrp_encoder_weights *w, int train, const 
 // What the encoder phase of vrp_rollout launches for this shape (profiles, bench line).
 extern "C" const char *vrp_encoder_kernel_name(const vrp_encoder_weights *w, int train, int B, int N) {
   if (!w) return "?";
+  // (vrp_rollout_encode, which bench.py times, never takes the tables tail: vrp_rollout launches
+  // encoder_stack_tables_x3_kernel<3> instead where stack_tables_applies)
   if (encoder_stack_applies(w, train, B, N))
     return encoder_stack_x3_applies(w) ? "encoder_stack_x3_kernel<3>" : "encoder_stack_kernel<3>";
   const int R = B * N;
@@ -3630,7 +3848,7 @@ static int encoder_layers(const vrp_encoder_weights *w, int train, int B, int N,
   if (encoder_stack_applies(w, train, B, N)) {
     StackSetup su = {};
     StackEpilogue ep = {};
-    if (encoder_stack_x3_applies(w)) return launch_encoder_stack_x3<3>(w, cur, ws.norm, emb, B, N, su, ep, st);
+    if (encoder_stack_x3_applies(w)) return launch_encoder_stack_x3<3>(w, cur, ws.norm, emb, B, N, su, ep, nullptr, st);
     return launch_encoder_stack<3>(w, cur, ws.norm, emb, B, N, su, ep, st);
   }
   for (int l = 0; l < w->num_layers; ++l) {
