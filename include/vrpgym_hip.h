@@ -30,7 +30,7 @@ extern "C" {
 
 /* Version of this header's struct layouts and entry points: vrp_abi_version() of a matching
  * library returns it; the shipped binding (vrpgym_hip/_lib.py: ABI_VERSION) refuses any other. */
-#define VRP_ABI_VERSION 8
+#define VRP_ABI_VERSION 9
 
 #define VRP_KIND_TSP 0
 #define VRP_KIND_VRP 1
@@ -288,6 +288,46 @@ int vrp_rollout_steps_range(int kind, const void *derived, const vrp_decoder_wei
                             const vrp_env *env, const float *emb, void *dec_workspace,
                             const vrp_rollout_io *io, int t_begin, int t_end, int max_steps,
                             int flags, void *stream);
+
+/* ---- best-of-K sampled decoding: K tours per instance from one encoding ---- */
+/* Outputs and noise of vrp_rollout_multi.  V = K * B virtual elements, element j = k * B + b being
+ * sample k of instance b, so a (K,B) array is indexed by j. */
+typedef struct vrp_multi_io {
+  float *all_loss;        /* (K,B) fp32 sum of -distance per sample   graph_tsp_agent.py:85      */
+  float *all_logp;        /* (K,B) fp32 sum of log-prob per sample    graph_tsp_agent.py:86      */
+  int32_t *notdone;       /* (max_steps+1) as vrp_rollout_io.notdone, over the V elements        */
+  int64_t *all_actions;   /* (max_steps,V) every sample's chosen nodes                           */
+  float *step_logp;       /* (max_steps,V) per-step log-prob, or NULL                            */
+  const float *noise;     /* (max_steps,V,N) Exp(1) noise (parity runs: what the reference draws */
+                          /*   on the tiled batch), or NULL                                      */
+  uint64_t noise_seed;    /* noise == NULL: in-kernel Philox noise, counter = (j, node, step)    */
+  int32_t *best_k;        /* (B) lowest k among the largest all_loss[k][b]                       */
+  float *acc_loss;        /* (B) all_loss of the chosen sample                                   */
+  float *acc_logp;        /* (B) all_logp of the chosen sample                                   */
+  int64_t *actions;       /* (max_steps,B) the chosen samples' tours                             */
+  float logit_clip;       /* as vrp_rollout_io.logit_clip                                        */
+} vrp_multi_io;
+
+/* Bytes of the per-element workspace of vrp_rollout_multi (visited rows, both mask buffers,
+ * current / last / first node, fp64 load for V = K * B elements, and the first-node score table
+ * of the B instances); a pure function of the shape, 0 for an invalid one. */
+int64_t vrp_multi_workspace_bytes(int kind, int B, int N, int K);
+
+/* R1 x K  TSPModel/VRPModel/IRPModel.forward (agents/graph_tsp_agent.py:61-92,
+ * graph_vrp_agent.py:52-83, graph_irp_agent.py:54-105) in eval mode, sampling
+ * (graph_decoder.py:100-107), on a virtual batch in which each of the env's B instances appears
+ * K times -- QUIRK D3 (graph_decoder.py:93) and the batch-wide done flag (tsp.py:95) couple the
+ * V = K * B elements -- followed by a per-instance choice of the cheapest tour.  Mask init,
+ * features, encoder and prologue run ONCE on the B instances (the same launches as vrp_rollout,
+ * running-statistics BatchNorm), then the first-node score table, max_steps multi-sample steps (one
+ * launch each) and the selection, all on `stream`.  The env's (B,N) state is read at the start
+ * (honouring VRP_ENV_RESET_ON_ROLLOUT) and written once at the end: the chosen tour's final
+ * visited row as its last env.step left it, current_location and load.  Supported: 3 <= N <= 100,
+ * K >= 1, K * B <= 2^24, every kind.  dec_workspace as for vrp_rollout (B instances),
+ * multi_workspace of vrp_multi_workspace_bytes. */
+int vrp_rollout_multi(int kind, const vrp_encoder_weights *ew, void *derived, const vrp_env *env,
+                      int K, float *emb, void *enc_workspace, void *dec_workspace,
+                      void *multi_workspace, const vrp_multi_io *io, int max_steps, void *stream);
 
 /* E1  Host-side instance sampler, bit-exact with numpy's legacy global stream
  * (VRPGraph.__init__ gym_vrp/graph/vrp_graph.py:28-43 called B times,

@@ -68,6 +68,29 @@ class TSPModel(nn.Module):
             logp = runtime.attach_grad(self, env, res)
         return res.acc_loss, logp
 
+    def sample_best(self, env, K) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Best-of-K sampled decoding (runtime.rollout_best_of): K sampled tours per instance
+        from one encoding, eval mode only -> (acc_loss (B,), acc_log_prob (B,)) of the cheapest
+        tour of every instance.  A watched env (video, materialised sampler.graphs) gets the
+        chosen tours replayed through env.replay_tour, like the greedy evaluation."""
+        if env.KIND not in self.ENV_KINDS:
+            raise TypeError(f"{type(self).__name__} cannot drive a {type(env).__name__}")
+        watched = env.video_save_path is not None or env.sampler._graphs is not None
+        if watched:
+            # the episode starts on the instances in place: bring the host-visible state there
+            # first, so that the snapshot replay_tour restores is the episode's start
+            env._reset_state()
+            env._step_count = 0
+            env._last_rollout = None
+        start = env.current_location if watched else None
+        before = env.snapshot_state() if env.video_save_path is not None else None
+        res = runtime.rollout_best_of(self, env, K, noise_mode=self.sampling_noise)
+        self.last_rollout = res
+        self.decoder.reset()
+        if watched:
+            env.replay_tour(start, res.actions.cpu().numpy(), before)
+        return res.acc_loss, res.acc_logp
+
 
 class TSPAgent:
     _MODEL = TSPModel
@@ -169,11 +192,16 @@ class TSPAgent:
             loss_b, _ = self.target_model(env_baseline, rollouts[0])
         return loss, loss_b, log_prob
 
-    def evaluate(self, env):
-        """Greedy rollout of the current model, eval-mode BN (graph_tsp_agent.py:257-273)."""
+    def evaluate(self, env, samples=None):
+        """Greedy rollout of the current model, eval-mode BN (graph_tsp_agent.py:257-273).
+        samples=K (an integer >= 1): best-of-K sampled decoding instead -- the loss of the cheapest
+        of K sampled tours per instance (TSPModel.sample_best)."""
         self.model.eval()
         with torch.no_grad():
-            loss, _ = self.model(env, rollout=True)
+            if samples is not None:
+                loss, _ = self.model.sample_best(env, samples)
+            else:
+                loss, _ = self.model(env, rollout=True)
         return loss
 
     def baseline_update(self, env, batch_steps: int = 3):

@@ -139,15 +139,9 @@ def _buf(owner, tag, device, nbytes):
     return t
 
 
-def workspaces(model, env):
-    """(encoder scratch, decoder per-episode workspace) private to this (model, env) pair:
-    the decoder workspace holds the episode's tables, so the model and the baseline model
-    (or two envs of one model) must not share it when they run on different streams.  The
-    env owns the tensors (they die with it); the model is referenced weakly."""
-    lib = hip.lib()
-    dev = _dev(model)
-    ew = encoder_struct(model.encoder)
-    B, N = env.batch_size, env.num_nodes
+def _ws_slot(model, env):
+    """The scratch dict private to this (model, env) pair.  The env owns it (the tensors die with
+    the env); the model is referenced weakly."""
     per_env = env.__dict__.setdefault("_ws", {})
     key = id(model)
     slot = per_env.get(key)
@@ -156,8 +150,20 @@ def workspaces(model, env):
             for k in [k for k, v in per_env.items() if v[0]() is None]:
                 del per_env[k]
         slot = per_env[key] = (weakref.ref(model), {})
-    enc = _buf(slot[1], "enc", dev, lib.vrp_encoder_workspace_bytes(B, N, ew.hidden))
-    dec = _buf(slot[1], "dec", dev, lib.vrp_decoder_workspace_bytes(env.KIND, B, N))
+    return slot[1]
+
+
+def workspaces(model, env):
+    """(encoder scratch, decoder per-episode workspace) private to this (model, env) pair:
+    the decoder workspace holds the episode's tables, so the model and the baseline model
+    (or two envs of one model) must not share it when they run on different streams."""
+    lib = hip.lib()
+    dev = _dev(model)
+    ew = encoder_struct(model.encoder)
+    B, N = env.batch_size, env.num_nodes
+    slot = _ws_slot(model, env)
+    enc = _buf(slot, "enc", dev, lib.vrp_encoder_workspace_bytes(B, N, ew.hidden))
+    dec = _buf(slot, "dec", dev, lib.vrp_decoder_workspace_bytes(env.KIND, B, N))
     return enc, dec
 
 
@@ -688,6 +694,127 @@ def rollout(model, env, greedy, train=False, forced=None, noise=None, trace=Fals
         torch.set_rng_state(gen_state)
         host_noise(T, B, N)
     env._last_rollout = res  # env.step_count adds its T lazily
+    if ROLLOUT_LOG is not None:
+        ROLLOUT_LOG.append(RolloutSteps(res))
+    return res
+
+
+class BestOfResult:
+    """Device tensors of one best-of-K episode (`rollout_best_of`): K sampled tours per instance
+    from one encoding, element j = k * B + b of the virtual batch being sample k of instance b.
+    all_loss / all_logp (K,B) fp32, best_k (B,) int32 = the lowest k among the largest
+    all_loss[k, b], acc_loss / acc_logp (B,) of the chosen samples, actions (T,B) int64 their
+    tours; with trace=True also all_actions (T,V) and step_logp (T,V).  `T` (steps until the
+    virtual batch's `done`) and everything cut to T rows need a stream sync and are read lazily."""
+
+    def __init__(self, all_loss, all_logp, best_k, acc_loss, acc_logp, notdone, actions_full,
+                 all_actions_full, step_logp_full, emb, max_steps, K, trace):
+        self.all_loss, self.all_logp, self.best_k = all_loss, all_logp, best_k
+        self.acc_loss, self.acc_logp, self.notdone, self.emb = acc_loss, acc_logp, notdone, emb
+        self.max_steps, self.K = max_steps, K
+        self._actions, self._all_actions, self._step_logp = actions_full, all_actions_full, step_logp_full
+        self._trace = trace
+        self._T = None
+
+    T = RolloutResult.T
+
+    @property
+    def actions(self):
+        return self._actions[: self.T]
+
+    @property
+    def all_actions(self):
+        return self._all_actions[: self.T] if self._trace else None
+
+    @property
+    def step_logp(self):
+        return self._step_logp[: self.T] if self._trace else None
+
+
+def rollout_best_of(model, env, K, noise=None, noise_mode="device", trace=False):
+    """Best-of-K sampled decoding: the reference's sampled rollout (TSPModel.forward with
+    rollout=False, eval mode) on a virtual batch of V = K * B elements in which every instance of
+    `env` appears K times -- QUIRK D3 and the batch-wide `done` couple the V elements -- followed
+    by a per-instance choice of the cheapest tour.  The encoder and the decoder prologue run once
+    on the B instances (vrp_rollout_multi).  The episode starts on the instances in place
+    (visited := 0, current_location := depots, load := 1); afterwards the env holds the chosen
+    tours' final state.  noise_mode="host": `empty((V, N)).exponential_(1)` per step from the CPU
+    generator, which is left advanced by T steps; "device": in-kernel Philox noise keyed by one
+    seed from the CPU generator, counter = element j; `noise`: an explicit (T, V, N) tensor."""
+    dev = _require_cuda(model)
+    if model.training:
+        raise ValueError("rollout_best_of needs the model in eval mode: with batch-statistics "
+                         "BatchNorm the encoding of an instance depends on the rest of the batch, "
+                         "so K samples cannot share one encoding (call model.eval())")
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"rollout_best_of: K={K}, needs K >= 1")
+    lib = hip.lib()
+    kind = env.KIND
+    if str(env._device) != str(dev):
+        raise RuntimeError(f"env is on {env._device} but the model on {dev}")
+    B, N = env.batch_size, env.num_nodes
+    V = K * B
+    ew = encoder_struct(model.encoder)
+    derived = decoder_derived(model.decoder, kind)
+    max_steps = max_steps_for(kind, N)
+    stream = hip.current_stream(dev)
+    enc_ws, dec_ws = workspaces(model, env)
+    nbytes = int(lib.vrp_multi_workspace_bytes(kind, B, N, K))
+    multi_ws = _buf(_ws_slot(model, env), "multi", dev, max(nbytes, 256))
+    f32 = dict(dtype=torch.float32, device=dev)
+    emb = torch.empty((B, N, EMB), **f32)
+    all_loss, all_logp = torch.empty((K, B), **f32), torch.empty((K, B), **f32)
+    acc_loss, acc_logp = torch.empty((B,), **f32), torch.empty((B,), **f32)
+    best_k = torch.empty((B,), dtype=torch.int32, device=dev)
+    notdone = torch.empty((max_steps + 1,), dtype=torch.int32, device=dev)
+    all_actions = torch.zeros((max_steps, V), dtype=torch.int64, device=dev)
+    actions = torch.empty((max_steps, B), dtype=torch.int64, device=dev)
+    io = hip.MultiIO()
+    io.all_loss, io.all_logp, io.notdone = all_loss.data_ptr(), all_logp.data_ptr(), notdone.data_ptr()
+    io.all_actions, io.actions, io.best_k = all_actions.data_ptr(), actions.data_ptr(), best_k.data_ptr()
+    io.acc_loss, io.acc_logp = acc_loss.data_ptr(), acc_logp.data_ptr()
+    step_logp = None
+    if trace:
+        step_logp = torch.zeros((max_steps, V), **f32)
+        io.step_logp = step_logp.data_ptr()
+    keep, gen_state = [], None
+    if noise is None and noise_mode != "host":
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        first = int(getattr(env, "_slice", slice(0, 0)).start or 0)
+        seed ^= (first * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+        io.noise_seed = seed | 1
+    else:
+        if noise is None:
+            gen_state = torch.get_rng_state()
+            noise = host_noise(max_steps, V, N)
+        noise = torch.as_tensor(noise, dtype=torch.float32).to(dev).contiguous()
+        if noise.dim() != 3 or tuple(noise.shape[1:]) != (V, N):
+            raise ValueError(f"rollout_best_of: noise must be (T, {V}, {N}), got {tuple(noise.shape)}")
+        if noise.shape[0] < max_steps:
+            pad = torch.ones((max_steps - noise.shape[0], V, N), device=dev)
+            noise = torch.cat([noise, pad]).contiguous()
+        keep.append(noise)
+        io.noise = noise.data_ptr()
+    env._sync_positions()
+    env._parity = 0
+    cenv = env._cenv()
+    cenv.flags = 1              # VRP_ENV_RESET_ON_ROLLOUT: the episode starts here
+    env._step_count = 0
+    env._last_rollout = None
+    hip.check(lib.vrp_rollout_multi(kind, C.byref(ew), derived.data_ptr(), C.byref(cenv), K,
+                                    emb.data_ptr(), enc_ws.data_ptr(), dec_ws.data_ptr(),
+                                    multi_ws.data_ptr(), C.byref(io), max_steps, stream))
+    env._mask_fresh = False     # visited as the last env.step left it; the fix-ups come lazily
+    res = BestOfResult(all_loss, all_logp, best_k, acc_loss, acc_logp, notdone, actions,
+                       all_actions, step_logp, emb, max_steps, K, trace)
+    res._keep = keep
+    if gen_state is not None:
+        # leave the CPU generator where the reference would on the tiled batch: T draws
+        T = res.T
+        torch.set_rng_state(gen_state)
+        host_noise(T, V, N)
+    env._last_rollout = res     # env.step_count adds its T lazily
     if ROLLOUT_LOG is not None:
         ROLLOUT_LOG.append(RolloutSteps(res))
     return res

@@ -65,6 +65,38 @@ static StepThrottle *step_throttle(hipStream_t st) {
   return &t;
 }
 
+// The paced launch loop shared by vrp_rollout_steps_range and vrp_rollout_multi: launch(t) for
+// t_begin <= t < t_end; with a throttle the host stays at most two chunks of STEP_CHUNK launches
+// ahead of the device from step tmin on and stops at the first chunk whose last step reported
+// every graph finished (notdone[t] comes back through a pinned word).
+template <typename Launch>
+static int paced_step_loop(StepThrottle *th, int tmin, int t_begin, int t_end,
+                           const int32_t *notdone, hipStream_t st, Launch launch) {
+  int queued = 0;   // checkpoints recorded so far
+  for (int t = t_begin; t < t_end; ++t) {
+    if (th && t >= tmin + 2 * STEP_CHUNK && (t - tmin) % STEP_CHUNK == 0) {
+      // checkpoint i = (t - tmin) / STEP_CHUNK - 2 covers step tmin + STEP_CHUNK (i + 1) - 1
+      const int i = (t - tmin) / STEP_CHUNK - 2;
+      if (i < queued) {
+        if (hipEventSynchronize(th->ev[i % 4]) != hipSuccess) { (void)hipGetLastError(); th = nullptr; }
+        else if (th->flags[i % 4] == 0) break;   // that step found every graph finished
+      }
+    }
+    if (int r = launch(t)) return r;
+    if (th && t >= tmin && (t - tmin + 1) % STEP_CHUNK == 0) {
+      const int i = queued % 4;
+      if (hipMemcpyAsync(&th->flags[i], notdone + t, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipEventRecord(th->ev[i], st) != hipSuccess) {
+        (void)hipGetLastError();
+        th = nullptr;
+      } else {
+        ++queued;
+      }
+    }
+  }
+  return 0;
+}
+
 extern "C" int vrp_rollout_steps_range(int kind, const void *derived,
                                        const vrp_decoder_weights *dw, const vrp_env *env,
                                        const float *emb, void *dec_workspace,
@@ -111,32 +143,9 @@ extern "C" int vrp_rollout_steps_range(int kind, const void *derived,
   if (kind != VRP_KIND_TSP && t_end == max_steps && t_begin <= tmin &&
       max_steps - tmin >= 2 * STEP_CHUNK && io->notdone && !(flags & VRP_STEP_DECODE_ONLY))
     th = step_throttle((hipStream_t)stream);
-  int queued = 0;   // checkpoints recorded so far
-  for (int t = t_begin; t < t_end; ++t) {
-    if (th && t >= tmin + 2 * STEP_CHUNK && (t - tmin) % STEP_CHUNK == 0) {
-      // checkpoint i = (t - tmin) / STEP_CHUNK - 2 covers step tmin + STEP_CHUNK (i + 1) - 1
-      const int i = (t - tmin) / STEP_CHUNK - 2;
-      if (i < queued) {
-        if (hipEventSynchronize(th->ev[i % 4]) != hipSuccess) { (void)hipGetLastError(); th = nullptr; }
-        else if (th->flags[i % 4] == 0) break;   // that step found every graph finished
-      }
-    }
-    if (int r = vrp_decode_step(kind, derived, dw, env, emb, dec_workspace, io, t, max_steps,
-                                flags, stream))
-      return r;
-    if (th && t >= tmin && (t - tmin + 1) % STEP_CHUNK == 0) {
-      const int i = queued % 4;
-      if (hipMemcpyAsync(&th->flags[i], io->notdone + t, sizeof(int32_t), hipMemcpyDeviceToHost,
-                         (hipStream_t)stream) != hipSuccess ||
-          hipEventRecord(th->ev[i], (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        th = nullptr;
-      } else {
-        ++queued;
-      }
-    }
-  }
-  return 0;
+  return paced_step_loop(th, tmin, t_begin, t_end, io->notdone, (hipStream_t)stream, [&](int t) {
+    return vrp_decode_step(kind, derived, dw, env, emb, dec_workspace, io, t, max_steps, flags, stream);
+  });
 }
 
 static int rollout_step_loop(int kind, const void *derived, const vrp_decoder_weights *dw,
@@ -231,4 +240,52 @@ extern "C" int vrp_rollout(int kind, const vrp_encoder_weights *ew, const vrp_de
   return rollout_step_loop(kind, derived, dw, env, emb, dec_workspace, io, max_steps,
                            sample & (VRP_STEP_SAMPLE | VRP_STEP_TILE_KERNEL | VRP_STEP_TABLE_KERNEL |
                                      VRP_STEP_THROUGHPUT_KERNEL | VRP_STEP_NO_PERSISTENT), stream);
+}
+
+// ---- best-of-K sampled decoding (decoder_multi.hip) ------------------------------------------
+int vrp_multi_tables(int kind, const void *derived, int B, int N, const float *emb,
+                     void *dec_workspace, void *multi_workspace, int K, hipStream_t st);
+int vrp_multi_init(int kind, const vrp_env *env, void *dec_workspace, void *multi_workspace,
+                   const vrp_multi_io *io, int K, int max_steps, hipStream_t st);
+int vrp_multi_step(int kind, const vrp_env *env, void *dec_workspace, void *multi_workspace,
+                   const vrp_multi_io *io, int K, int t, int max_steps, hipStream_t st);
+int vrp_multi_select(int kind, const vrp_env *env, void *dec_workspace, void *multi_workspace,
+                     const vrp_multi_io *io, int K, int max_steps, hipStream_t st);
+
+extern "C" int vrp_rollout_multi(int kind, const vrp_encoder_weights *ew, void *derived,
+                                 const vrp_env *env, int K, float *emb, void *enc_workspace,
+                                 void *dec_workspace, void *multi_workspace,
+                                 const vrp_multi_io *mio, int max_steps, void *stream) {
+  VRP_REQUIRE(env && mio && multi_workspace, "rollout_multi: NULL argument");
+  VRP_REQUIRE(kind >= VRP_KIND_TSP && kind <= VRP_KIND_IRP, "rollout_multi: kind=%d is not 0, 1 or 2", kind);
+  const int B = env->B, N = env->N;
+  VRP_REQUIRE(N >= 3 && N <= 100, "rollout_multi: N=%d outside the supported 3 <= N <= 100", N);
+  VRP_REQUIRE(K >= 1, "rollout_multi: K=%d, needs K >= 1", K);
+  VRP_REQUIRE(B >= 1 && (int64_t)K * B <= (1 << 24),
+              "rollout_multi: K*B=%lld outside the supported 1 <= K*B <= 2^24", (long long)K * B);
+  VRP_REQUIRE(mio->all_loss && mio->all_logp && mio->notdone && mio->all_actions && mio->best_k &&
+                  mio->acc_loss && mio->acc_logp && mio->actions,
+              "rollout_multi: io has NULL outputs");
+  VRP_REQUIRE(mio->noise || mio->noise_seed, "rollout_multi: sampling needs io.noise or io.noise_seed");
+  hipStream_t st = (hipStream_t)stream;
+  // the B real instances: set-up kernel, encoder, prologue -- vrp_rollout's own launches, eval mode
+  // (acc_loss / acc_logp (B) are zeroed here and overwritten by the selection)
+  vrp_rollout_io io = {};
+  io.acc_loss = mio->acc_loss; io.acc_logp = mio->acc_logp; io.notdone = mio->notdone;
+  int constants_done = 0;
+  if (int r = rollout_encode(kind, ew, derived, env, 0, emb, enc_workspace, dec_workspace, &io,
+                             max_steps, true, &constants_done, stream)) return r;
+  if (int r = vrp_decode_prologue_ex(kind, derived, B, N, emb, dec_workspace, constants_done,
+                                     stream)) return r;
+  if (int r = vrp_multi_tables(kind, derived, B, N, emb, dec_workspace, multi_workspace, K, st)) return r;
+  if (int r = vrp_multi_init(kind, env, dec_workspace, multi_workspace, mio, K, max_steps, st)) return r;
+  // one launch per step, paced like vrp_rollout_steps_range's loop: from step N - 1 on a VRP / IRP
+  // call stays at most two chunks ahead of the device and stops at the first finished chunk
+  StepThrottle *th = nullptr;
+  const int tmin = N - 1;
+  if (kind != VRP_KIND_TSP && max_steps - tmin >= 2 * STEP_CHUNK) th = step_throttle(st);
+  if (int r = paced_step_loop(th, tmin, 0, max_steps, mio->notdone, st, [&](int t) {
+        return vrp_multi_step(kind, env, dec_workspace, multi_workspace, mio, K, t, max_steps, st);
+      })) return r;
+  return vrp_multi_select(kind, env, dec_workspace, multi_workspace, mio, K, max_steps, st);
 }

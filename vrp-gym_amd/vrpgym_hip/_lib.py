@@ -4,7 +4,7 @@ import os
 
 KIND_TSP, KIND_VRP, KIND_IRP = 0, 1, 2
 MAX_LAYERS = 16   # VRP_MAX_LAYERS
-ABI_VERSION = 8   # include/vrpgym_hip.h: VRP_ABI_VERSION (struct layouts below mirror that header)
+ABI_VERSION = 9   # include/vrpgym_hip.h: VRP_ABI_VERSION (struct layouts below mirror that header)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -70,6 +70,14 @@ class RolloutIO(C.Structure):
                                     "load_trace")] + [("noise_seed", C.c_uint64), ("logit_clip", C.c_float)]
 
 
+class MultiIO(C.Structure):
+    """struct vrp_multi_io"""
+    _fields_ = ([(n, c_vp) for n in ("all_loss", "all_logp", "notdone", "all_actions", "step_logp",
+                                     "noise")] + [("noise_seed", C.c_uint64)] +
+                [(n, c_vp) for n in ("best_k", "acc_loss", "acc_logp", "actions")] +
+                [("logit_clip", C.c_float)])
+
+
 class DecoderGrads(C.Structure):
     """struct vrp_decoder_grads"""
     _fields_ = [(n, c_vp) for n in (
@@ -109,6 +117,9 @@ def _declare(lib):
                                     i32, i32, vp]),
         "vrp_rollout_steps_range": (i32, [i32, vp, P(DecoderWeights), P(Env), vp, vp,
                                           P(RolloutIO), i32, i32, i32, i32, vp]),
+        "vrp_multi_workspace_bytes": (i64, [i32, i32, i32, i32]),
+        "vrp_rollout_multi": (i32, [i32, P(EncoderWeights), vp, P(Env), i32, vp, vp, vp, vp,
+                                    P(MultiIO), i32, vp]),
         "vrp_draw_instances_host": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "vrp_draw_instances_host_range": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "vrp_debug_exp1_from_bits": (i32, [vp, vp, i32, vp]),
